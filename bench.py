@@ -8,16 +8,23 @@ One step = the whole hot path over one synthetic graph already resident in HBM:
   -> makeKids + partition_tree forwardPartition (k parts) on rank 0
 
 (reference: graph2tree.cpp:161-216 `-ir` + partition_tree.cpp:130-143).
-After the timed steps the ECV(down)/balance evaluator (partition.cpp:475-521) is timed
-on its own ("timed and rooflined separately"): on one GPU over all
+A plain run sets up the graph, warms up, times the steps and prints one JSON line (its
+phases and rooflines come from the timed steps' own HIP events and the committed PMC
+profile, no further run); `--dump-outputs DIR` also writes what the last step returned.
+Everything else is behind `--full`: the evaluator, the CPU baseline with `matches_gpu`
+and the merged tree's cross-check.
+
+With `--full`, after the timed steps the ECV(down)/balance evaluator (partition.cpp:475-521)
+is timed on its own ("timed and rooflined separately"): on one GPU over all
 records; on N GPUs sharded — parts broadcast (Partition::mpi_sync), per-shard owner
 bitsets, a binomial OR-reduction to rank 0, one node pass.
 
 Every computation runs in libsheep_hip.so's HIP kernels; the reference's own lib/ code
-(oracle/_ref, built from /root/reference) is only timed as the `cpu_baseline` leg
+(oracle/_ref, built by oracle/ref/Makefile) is only timed as `--full`'s `cpu_baseline` leg
 (rank 0, N=1) on a bounded sample.
 
     python bench.py [--gpus N --steps K --warmup W --scale 26 --ef 16 --k 64 --shuffle]
+                    [--dump-outputs DIR] [--full]
 
 For N > 1 launch with torch.distributed.run (one process per GPU, RCCL over xGMI).
 The graph is fixed as N grows (edge shards of one RMAT graph): "scaling": "strong".
@@ -76,7 +83,15 @@ def parse():
                          "thread of its own (a stream of graphs; 0: off)")
     ap.add_argument("--shuffle", action="store_true",
                     help="records in a random order, half with tail/head swapped (a generic edge list)")
-    ap.add_argument("--eval-reps", type=int, default=3, help="timed evaluator runs (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: the timed evaluator "
+                         "(--eval-reps), the reference CPU baseline with `matches_gpu` (--no-cpu-baseline drops it) "
+                         "and the merged tree's cross-check (--shards, --gpus N; --no-verify drops it).  A run without "
+                         "--full sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (sequence, tree, parts; a seeded "
+                         "sample of at most 2^20 elements of each) as DIR/<name>.npy in float64 (rank 0)")
+    ap.add_argument("--eval-reps", type=int, default=3, help="--full: timed evaluator runs (0: skip)")
     ap.add_argument("--eval-records", action="store_true",
                     help="one GPU: also time the record evaluator (sheep_evaluate) beside the step-edge one")
     ap.add_argument("--cpu-scale", type=int, default=None,
@@ -104,7 +119,10 @@ def parse():
     ap.add_argument("--no-verify", dest="verify", action="store_false",
                     help="skip the after-timing check of the merged tree (N > 1: against the whole-graph tree; "
                          "--shards: against the binomial pairwise merges of the same shard trees)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps counts the timed steps (at least 1); --warmup is 0 or more")
+    return a
 
 
 def make_records(a, seed, ctx):
@@ -399,8 +417,12 @@ def main():
                                        if k in phases}}
         per_rank = sdist.gather_objects(mine)
 
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, s, tree, res)
+
     evaluator = None
-    if a.eval_reps > 0:
+    if a.full and a.eval_reps > 0:
         evaluator = time_evaluator(a, ctx_last if conc is not None else ctx, group, shard, subs, s, res, rank, world,
                                    dev, barrier)
     ctx.timing(False)
@@ -409,7 +431,7 @@ def main():
 
     verified = None
     checks = {}
-    if a.verify and (world > 1 or a.shards > 1):
+    if a.full and a.verify and (world > 1 or a.shards > 1):
         if rank == 0:
             checks = verify_tree(a, seed, ctx, shard, subs, s, tree, stack[0], world)
             verified = all(checks.values())
@@ -477,7 +499,10 @@ def main():
         if per_rank is not None:
             out["per_rank"] = per_rank
         out.update(checks)   # verified_vs_whole_graph / verified_vs_pairwise_merges: the checks that ran
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        out["full"] = a.full
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a, ctx, (s, tree, res), seed, shard)
     del shard
     if group is not None:
@@ -488,6 +513,42 @@ def main():
         print(json.dumps(out), file=json_out, flush=True)
     if verified is False:
         sys.exit(1)
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of each dumped array (5 arrays x 8 B x 2^20 = 40 MiB at most)
+
+
+def dump_outputs(path, s, tree, res):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as
+    float64 .npy files (every u32 / i16 value is exact in a double): the degree sequence
+    (`seq`, its index `pos`), the elimination tree (`tree_parent`, `tree_pst`), the parts
+    (`parts`) and the scalars of the step (`summary`: tree nodes, vertex slots, parts
+    created, first and second part size, largest component, total weight).  An array of
+    more than DUMP_SAMPLE elements is sampled at sorted indices drawn once from a fixed
+    seed and the array's own length, so two builds that compute the same arrays write the
+    same files."""
+    import numpy as np
+    import torch
+
+    def sample(x):                                              # rows of x, on the host
+        if x.shape[0] > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20260).integers(0, x.shape[0], DUMP_SAMPLE))
+            x = x[torch.from_numpy(idx).to(x.device)]
+        return np.ascontiguousarray(x.cpu().numpy())
+
+    def u32(x):
+        return sample(x).view(np.uint32).astype(np.float64)
+
+    os.makedirs(path, exist_ok=True)
+    nodes = u32(tree[:s.n])
+    arrays = {"seq": u32(s.seq[:s.n]), "pos": u32(s.pos[:s.pos_size]),
+              "tree_parent": nodes[:, 0].copy(), "tree_pst": nodes[:, 1].copy(),
+              "parts": sample(res.parts).astype(np.float64),
+              "summary": np.array([s.n, s.pos_size, res.created, res.first_size, res.second_size,
+                                   res.max_component, res.total_weight], dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 def verify_tree(a, seed, ctx, shard, subs, s, tree, stacked, world):

@@ -11,6 +11,6 @@ HB=$!
 trap 'kill $HB' EXIT
 for cfg in "4 1" "4 2" "2 1"; do
   set -- $cfg
-  timeout -k 10 600 python -u bench.py --scale 28 --k 256 --shards $1 --streams $2 --steps 2 --warmup 1 \
+  timeout -k 10 600 python -u bench.py --full --scale 28 --k 256 --shards $1 --streams $2 --steps 2 --warmup 1 \
     --no-cpu-baseline --eval-reps 1 > $O/c5_sh$1_st$2.json 2> $O/c5_sh$1_st$2.err || exit 1
 done

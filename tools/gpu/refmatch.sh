@@ -9,8 +9,8 @@ mkdir -p $O && export HSA_ENABLE_IPC_MODE_LEGACY=0
 HB=$!
 trap 'kill $HB' EXIT
 if [ -n "$C4" ]; then
-  timeout -k 10 900 python -u bench.py --graph powerlaw --k 128 --steps 2 --warmup 1 --eval-reps 1 --cpu-same-graph \
+  timeout -k 10 900 python -u bench.py --full --graph powerlaw --k 128 --steps 2 --warmup 1 --eval-reps 1 --cpu-same-graph \
     --cpu-configs 16x1 > $O/c4.json 2> $O/c4.err || exit 1
 fi
-timeout -k 10 1080 python -u bench.py --scale 28 --k 256 --shards 2 --steps 2 --warmup 1 --eval-reps 1 --cpu-same-graph \
+timeout -k 10 1080 python -u bench.py --full --scale 28 --k 256 --shards 2 --steps 2 --warmup 1 --eval-reps 1 --cpu-same-graph \
   --cpu-configs 8x1 > $O/c5.json 2> $O/c5.err || exit 1
