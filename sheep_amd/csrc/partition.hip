@@ -880,22 +880,26 @@ __global__ void k_push_fringe(const uint32_t *__restrict__ parent, const uint8_t
 
 // ---- facts ---------------------------------------------------------------------------
 __global__ void k_facts_basic(const sheep_jnode *__restrict__ tree, uint64_t n, unsigned long long *__restrict__ f) {
-  // f[0] = sum pst, f[1] = max pst, f[2] = roots, f[3] = min id with pst > 2 (width > 3)
+  // f[0] = sum pst, f[1] = max pst, f[2] = roots, f[3] = min id with pst > 2 (width > 3),
+  // f[5] = max pst of a root: the edge height of a root without kids, which no tour reaches
+  // (k_root_eheight raises it by the paths below the roots that have kids)
   const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
-  uint64_t s = 0, mx = 0, r = 0, halo = ~0ull;
+  uint64_t s = 0, mx = 0, r = 0, halo = ~0ull, rmx = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
     sheep_jnode j = tree[i];
     s += j.pst_weight;
     mx = j.pst_weight > mx ? j.pst_weight : mx;
     r += j.parent == INVALID;
+    if (j.parent == INVALID && j.pst_weight > rmx) rmx = j.pst_weight;
     if (j.pst_weight > 2 && i < halo) halo = i;
   }
-  s = wave_sum(s); mx = wave_max(mx); r = wave_sum(r); halo = wave_min(halo);
+  s = wave_sum(s); mx = wave_max(mx); r = wave_sum(r); halo = wave_min(halo); rmx = wave_max(rmx);
   if ((threadIdx.x & 63) == 0) {
     atomicAdd(&f[0], (unsigned long long)s);
     atomicMax(&f[1], (unsigned long long)mx);
     atomicAdd(&f[2], (unsigned long long)r);
     atomicMin(&f[3], (unsigned long long)halo);
+    if (rmx) atomicMax(&f[5], (unsigned long long)rmx);
   }
 }
 // depth(c) = E1[tD] + 1;  path(c) = E2[tD] + pst(c);  per-root best path via the root
@@ -1529,8 +1533,7 @@ void tree_facts(Ctx &c, const sheep_jnode *tree, uint64_t n, sheep_facts_t *out)
   out->fill = 0;
   out->root_cnt = roots;
   out->vert_height = maxdepth + 1;   // a root alone has vheight 1
-  // kidless roots: eheight = own pst
-  out->edge_height = eheight;
+  out->edge_height = eheight;        // (k_facts_basic: a root without kids has its own pst)
   out->halo_id = halo == ~0ull ? INVALID : halo;
   out->core_id = 0;
 }
