@@ -29,6 +29,9 @@
  *                                 forwardPartition) and partition.h:135-143 (print counts)
  *   sheep_evaluate                partition.cpp:428-473 + :475-521 (both evaluators)
  *   sheep_facts                   jnode.cpp:256-290 (JNodeTable::Facts)
+ *   sheep_tree_widths             jtree.cpp:97 + jnode.h:230-260 (newUnion: the junction sets
+ *                                 of graph2tree -k -e -j; here only their sizes, width(id))
+ *   sheep_facts_widths            jnode.cpp:256-290 with those widths (width, fill, halo)
  *   sheep_rmat_generate           (new) synthetic Graph500-style RMAT .dat records
  */
 #ifndef SHEEP_HIP_H
@@ -44,7 +47,7 @@ extern "C" {
 /* ABI version: raised whenever a public struct changes size or layout or an entry point its
  * signature (INTEGRATION.md "ABI versions" lists the changes).  sheep_abi_version() returns the
  * library's; a caller built against another header should refuse to run. */
-#define SHEEP_ABI_VERSION 6
+#define SHEEP_ABI_VERSION 7
 int sheep_abi_version(void);
 
 #define SHEEP_OK 0
@@ -394,6 +397,29 @@ int sheep_mesh_selftest_stall(int rank, int world, const char *host, int port, i
 
 /* ---- tree facts (TREEFAQS) -------------------------------------------------------- */
 int sheep_facts(sheep_ctx *ctx, const sheep_jnode *tree_dev, uint64_t n, sheep_facts_t *out);
+
+/* ---- true widths (graph2tree -k -e -j) -----------------------------------------------
+ * width_dev[0, n) = 1 + |jxn(id)|: jxn(id) = the later vertices adjacent to id's subtree
+ * (jtree.cpp:97, jnode.h:230-260 width(id) with a jxn table) — the bag sizes of the
+ * junction tree, i.e. the column counts of the symbolic factor.  Only the sizes are
+ * computed (the reference materialises every set under a 1 GB cap, jtree.h:89).  Edges are
+ * the records in sequence positions; self-loops and records with an unsequenced end are
+ * dropped as the map drops them; a repeated edge counts once.  A neighbour >= pos_size of
+ * a sequenced vertex is SHEEP_ERR_RANGE, as in sheep_build_tree.
+ * tree_dev must be the tree of exactly these records under this sequence (a shard's tree,
+ * or a merge with only one shard's records, gives meaningless counts).  That cannot be
+ * verified in general; the call returns SHEEP_ERR_ARG when some edge's earlier end is not a
+ * descendant of its later end.  n == 0, nrec == 0 and all-self-loop inputs give widths of 1.
+ * Synchronises (the error flags).  Timers: "widths" and its passes "widths_tour",
+ * "widths_sort", "widths_lca", "widths_weights", "widths_sums". */
+int sheep_tree_widths(sheep_ctx *ctx, const sheep_xs1 *rec_dev, uint64_t nrec, const uint32_t *pos_dev,
+                      uint64_t pos_size, const sheep_jnode *tree_dev, uint64_t n, uint32_t *width_dev);
+/* JNodeTable::Facts (jnode.cpp:256-290) with the given widths: width = their maximum, fill =
+ * the sum of (width - pst_weight - 1) in wrapping unsigned 64-bit arithmetic (the
+ * reference's size_t; a multigraph makes single terms negative), halo = the first id with
+ * width > 3, core by the reference's running-maximum rule.  width_dev == NULL: sheep_facts. */
+int sheep_facts_widths(sheep_ctx *ctx, const sheep_jnode *tree_dev, uint64_t n, const uint32_t *width_dev,
+                       sheep_facts_t *out);
 
 /* ---- .dat partial loads (LLAMAGraph(filename, part, num_parts), graph_wrapper.h:43-63) ----
  * Host-only.  sheep_dat_range: records [*first_out, *first_out + *count_out) of a .dat file

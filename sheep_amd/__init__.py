@@ -15,6 +15,7 @@ Partition(seq,jnodes,k..)  :func:`partition`  (partition.cpp:50-157)
 Partition::print           :meth:`PartitionResult.print_text`  (partition.h:135-143)
 Partition::evaluate        :func:`evaluate`  (partition.cpp:428-521)
 JNodeTable::Facts          :func:`facts`  (jnode.cpp:256-290)
+JTree make_jxn / width(id) :func:`tree_widths`  (jtree.cpp:97, jnode.h:230-260)
 =========================  ======================================================
 
 Device memory is torch-allocated (``torch.cuda``), streams are torch's current
@@ -40,7 +41,7 @@ INVALID_PART = -1
 DEGREE_MODES = {"llama": 0, "dat": 1, "net": 2}
 EVAL_GRAPH, EVAL_DOWN, EVAL_UP = 1, 2, 4
 
-ABI_VERSION = 6   # include/sheep_hip.h SHEEP_ABI_VERSION
+ABI_VERSION = 7   # include/sheep_hip.h SHEEP_ABI_VERSION
 _ERRORS = {-1: ValueError, -2: RuntimeError, -3: IndexError, -4: RuntimeError, -5: MemoryError}
 
 
@@ -140,6 +141,8 @@ def lib() -> ctypes.CDLL:
         "sheep_evaluate": ([P, P, U64, P, U64, P, I32, ctypes.POINTER(_Eval)], I32),
         "sheep_evaluate_step": ([P, P, U64, P, U64, P, U64, P, I32, ctypes.POINTER(_Eval)], I32),
         "sheep_facts": ([P, P, U64, ctypes.POINTER(_Facts)], I32),
+        "sheep_tree_widths": ([P, P, U64, P, U64, P, U64, P], I32),
+        "sheep_facts_widths": ([P, P, U64, P, ctypes.POINTER(_Facts)], I32),
         "sheep_eval_sizes": ([I32, I32, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)], I32),
         "sheep_eval_num_parts": ([P, P, U64, ctypes.POINTER(ctypes.c_int32)], I32),
         "sheep_eval_shard": ([P, P, U64, P, U64, P, I32, I32, P, P], I32),
@@ -630,11 +633,32 @@ class Facts:
                 f"\tfill:{self.fill}\n")
 
 
-def facts(tree, ctx: Context | None = None) -> Facts:
+def facts(tree, widths=None, ctx: Context | None = None) -> Facts:
+    """JNodeTable::Facts; with `widths` (:func:`tree_widths`) width, fill and halo are those of
+    the true bag sizes instead of the placeholder 1 + pst_weight."""
     ctx = ctx or default_context()
     out = _Facts()
-    _check(lib().sheep_facts(ctx.handle, _ptr(tree), tree.shape[0], ctypes.byref(out)))
+    if widths is None:
+        _check(lib().sheep_facts(ctx.handle, _ptr(tree), tree.shape[0], ctypes.byref(out)))
+    else:
+        if widths.shape[0] != tree.shape[0]:
+            raise ValueError("one width per tree node")
+        _check(lib().sheep_facts_widths(ctx.handle, _ptr(tree), tree.shape[0], _ptr(widths), ctypes.byref(out)))
     return Facts(*[getattr(out, f) for f, _ in _Facts._fields_])
+
+
+def tree_widths(records, seq: Sequence, tree, nrec: int | None = None, ctx: Context | None = None):
+    """width(id) = 1 + |jxn(id)| per jnid (graph2tree -k -e -j; jtree.cpp:97, jnode.h:230-260):
+    device int32 tensor [n].  `tree` must be the tree of exactly these records under `seq`;
+    an edge whose earlier end is not below its later end raises ValueError."""
+    ctx = ctx or default_context()
+    t = _torch()
+    nrec = records.shape[0] if nrec is None else nrec
+    n = tree.shape[0]
+    out = t.empty(max(n, 1), dtype=t.int32, device=_dev(ctx))
+    _check(lib().sheep_tree_widths(ctx.handle, _ptr(records), nrec, _ptr(seq.pos), seq.pos_size, _ptr(tree), n,
+                                   _ptr(out)))
+    return out[:n]
 
 
 # ---------------------------------------------------------------------------------

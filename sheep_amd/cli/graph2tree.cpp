@@ -1,7 +1,7 @@
 // graph2tree — drop-in for chan150/sheep graph2tree.cpp (same getopt string, same
 // stdout lines, same .seq/.tre files) over libsheep_hip.so.
 //
-//   graph2tree input_graph [-s SEQ] [-o OUT] [-p K] [-l n/k] [-i] [-r] [-f] [-t] [-c] [-v]
+//   graph2tree input_graph [-s SEQ] [-o OUT] [-p K] [-l n/k] [-i] [-r] [-k -e -j] [-f] [-t] [-c] [-v]
 //
 // Phases (graph2tree.cpp:161-218): load the records into HBM, degree sequence (or -s
 // read), map (JTree on the GPU), [reduce], [partition], [TREEFAQS].  -i / -r select the
@@ -11,8 +11,11 @@
 // per-GPU partial trees, the merge on rank 0, the parts broadcast and per-rank partition
 // files, with the reference's file names (include/sheep_hip.h sheep_group_*).  With one
 // rank the single-GPU path runs.  -t prints every node (JTree::print, jtree.h:60-66) on
-// every rank.  Flags of the junction-tree experiments (-e -j -m -w -x) are rejected with a
-// message.
+// every rank.  -k -e -j (make_kids, make_pst, make_jxn, graph2tree.cpp:86-94) compute the true
+// widths 1 + |jxn(id)| of the whole graph's tree on one GPU (sheep_tree_widths): TREEFAQS and
+// the node lines then print them.  -j needs both -k and -e (JTree::Options::isValid,
+// jtree.h:100-107); -k and -e alone change nothing.  The width-limit experiments (-m -w -x)
+// are rejected with a message.
 #include <unistd.h>
 
 #include <cassert>
@@ -201,6 +204,7 @@ int main(int argc, char *argv[]) {
   const char *sequence_filename = "";
   const char *output_filename = "";
   bool verbose = false, do_faqs = false, do_print = false, do_validate = false;
+  JTree::Options jopts;
 
   opterr = 0;
   int opt;
@@ -216,12 +220,14 @@ int main(int argc, char *argv[]) {
       case 's': sequence_filename = optarg; break;
       case 'o': output_filename = optarg; break;
       case 'v': verbose = !verbose; break;
-      case 'k': break;   // make_kids: the kid table is always built on demand
+      case 'k': jopts.make_kids = !jopts.make_kids; break;   // (the kid table is built on demand either way)
+      case 'e': jopts.make_pst = !jopts.make_pst; break;     // (pst sets are never needed)
+      case 'j': jopts.make_jxn = !jopts.make_jxn; break;
       case 'd': break;
       case 'f': do_faqs = !do_faqs; break;
       case 't': do_print = !do_print; break;
       case 'c': do_validate = !do_validate; break;
-      case 'e': case 'j': case 'm': case 'w': case 'x':
+      case 'm': case 'w': case 'x':
         printf("Option -%c (junction-tree / width experiments) is not supported by this build.\n", opt);
         return 1;
       case '?':
@@ -240,6 +246,24 @@ int main(int argc, char *argv[]) {
     return 1;
   }
   const char *const graph_filename = argv[optind];
+  if (!jopts.isValid()) {   // the reference asserts (jtree.cpp:114)
+    printf("Option -j (junction sets) needs both -k and -e.\n");
+    return 1;
+  }
+  if (jopts.make_jxn && num_parts != 0) {   // a shard's tree has no widths of its own
+    printf("Option -j (junction sets) is not supported together with -l by this build.\n");
+    return 1;
+  }
+  if (jopts.make_jxn && (use_mpi_sort || use_mpi_reduce)) {
+    // the world's size as World::from_env will find it, before any rank opens a device or
+    // waits for a peer; the reference's merge drops jxn as well (jnode.cpp:174-201)
+    const int launched = launcher_env().size;
+    const size_t world = launched > 1 ? (size_t)launched : std::max<size_t>(env_devices().size(), 1);
+    if (world > 1) {
+      printf("Option -j (junction sets) is not supported together with -i / -r over more than one rank by this build.\n");
+      return 1;
+    }
+  }
   auto start_point = std::chrono::steady_clock::now();
 
   if (use_mpi_sort || use_mpi_reduce) {
@@ -286,7 +310,7 @@ int main(int argc, char *argv[]) {
     const double sort_s = seconds_since(start_point) - load_s;
     if (is_leader && (use_mpi_sort || strcmp(sequence_filename, "") == 0)) printf("Sorted in: %f seconds\n", sort_s);
 
-    JTree tree(graph, seq);
+    JTree tree(graph, seq, jopts);
     Context::get().sync();
     const double map_s = seconds_since(start_point) - sort_s - load_s;
     if (is_leader) printf("Mapped in: %f seconds\n", map_s);

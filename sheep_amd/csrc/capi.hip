@@ -48,6 +48,9 @@ void eval_combine(Ctx &c, uint64_t *bits, const uint64_t *bits_src, uint64_t wor
 void eval_finish(Ctx &c, const uint64_t *bits, const uint64_t *acc, uint64_t pos_size, const int16_t *parts, int what,
                  int nparts, sheep_eval *out);
 void tree_facts(Ctx &c, const sheep_jnode *tree, uint64_t n, sheep_facts_t *out);
+void tree_widths(Ctx &c, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *pos, uint64_t pos_size,
+                 const sheep_jnode *tree, uint64_t n, uint32_t *width);
+void tree_facts_widths(Ctx &c, const sheep_jnode *tree, uint64_t n, const uint32_t *width, sheep_facts_t *out);
 void edge_parts(Ctx &c, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *pos, uint64_t pos_size,
                 const int16_t *parts_vid, int16_t *out);
 void record_stats(Ctx &c, const sheep_xs1 *rec, uint64_t nrec, uint64_t *max_slot, uint64_t *loops);
@@ -514,6 +517,24 @@ int sheep_facts(sheep_ctx *ctx, const sheep_jnode *tree, uint64_t n, sheep_facts
   DeviceGuard dg(ctx);
   NEED(ctx && out && (tree || !n), "null argument");
   sheep::tree_facts(ctx->c, tree, n, out);
+  API_END
+}
+
+int sheep_tree_widths(sheep_ctx *ctx, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *pos, uint64_t pos_size,
+                      const sheep_jnode *tree, uint64_t n, uint32_t *width) {
+  API_BEGIN
+  DeviceGuard dg(ctx);
+  NEED(ctx && (rec || !nrec) && (pos || !pos_size) && ((tree && width) || !n), "null argument");
+  NEED(n < 0xFFFFFFFFull, "tree too large for 32-bit node ids");
+  sheep::tree_widths(ctx->c, rec, nrec, pos, pos_size, tree, n, width);
+  API_END
+}
+
+int sheep_facts_widths(sheep_ctx *ctx, const sheep_jnode *tree, uint64_t n, const uint32_t *width, sheep_facts_t *out) {
+  API_BEGIN
+  DeviceGuard dg(ctx);
+  NEED(ctx && out && (tree || !n), "null argument");
+  sheep::tree_facts_widths(ctx->c, tree, n, width, out);
   API_END
 }
 

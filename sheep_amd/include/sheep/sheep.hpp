@@ -4,7 +4,7 @@
 //
 //   reference (file:line)                         here
 //   GraphWrapper / LLAMAGraph (graph_wrapper.h:43)  GraphWrapper   (records resident in HBM)
-//   degreeSequence / mpiSequence (sequence.h:52,65) degreeSequence (LLAMA degrees, on the GPU)
+//   degreeSequence / mpiSequence (sequence.h:52-63, 65-93) degreeSequence (LLAMA degrees, on the GPU)
 //   fileSequence (sequence.h:95-128)              fileSequence   (file degrees, on the GPU)
 //   readSequence / writeSequence (:153-184)       readSequence / writeSequence (host text I/O)
 //   JNodeTable (jnode.h:48-297)                   JNodeTable     (host nodes + device mirror)
@@ -367,6 +367,8 @@ class JNodeTable {
     end_id_ = n;
     dev_.reset();
     if (kids_) { sheep_kids_destroy(kids_); kids_ = nullptr; }
+    widths_.clear();
+    wdev_.reset();
   }
 
   // merge (jnode.cpp:174-201): Liu over the union of both parent-edge sets, pst summed.
@@ -378,19 +380,32 @@ class JNodeTable {
     assign_from_device(out, n, std::max<jnid_t>(max_id(), n));
   }
 
+  // make_jxn (jtree.cpp:97, jnode.h:230-253) as far as anything reads it: the sizes of the
+  // junction sets of this tree's own records under its sequence (sheep_tree_widths).  The
+  // sets themselves are never built and, like the reference's, never saved.
+  void computeWidths(const sheep_xs1 *rec_dev, uint64_t nrec, const uint32_t *pos_dev, uint64_t pos_size) {
+    wdev_.reset(new DeviceArray<uint32_t>(end_id_));
+    check(sheep_tree_widths(ctx(), rec_dev, nrec, pos_dev, pos_size, device(), end_id_, wdev_->get()));
+    widths_.resize(end_id_);
+    if (end_id_) wdev_->download(widths_.data(), end_id_);
+  }
+  bool hasWidths() const { return wdev_ != nullptr; }
+  // width(id) (jnode.h:258-260): 1 + |jxn(id)| once computed, else 1 + pst_weight(id)
+  size_t width(jnid_t id) const { return hasWidths() ? widths_.at(id) : (size_t)1 + nodes_.at(id).pst_weight; }
+  const std::vector<uint32_t> &widths() const { return widths_; }
+
   Facts getFacts() const {
     Facts x;
-    check(sheep_facts(ctx(), device(), end_id_, &x.f));
+    check(sheep_facts_widths(ctx(), device(), end_id_, hasWidths() ? wdev_->get() : nullptr, &x.f));
     return x;
   }
 
-  // JNodeTable::print(id) (jnode.h:263-267) on the default path: no junction data, so
-  // width = 1 + pst (jnode.h:258-260), and pre_weight is 0 without USE_PRE_WEIGHT
-  // (defs.h:62, jnode.h:139-153).
-  void print(jnid_t id) const { printNode(nodes_.at(id)); }
-  static void printNode(const sheep_jnode &x) {
-    printf("%6zu:w%6zu:pre%6zu:pst        ->[%4zu]\n", (size_t)1 + x.pst_weight, (size_t)0, (size_t)x.pst_weight,
-           (size_t)x.parent);
+  // JNodeTable::print(id) (jnode.h:263-267): width(id) as above, and pre_weight is 0
+  // without USE_PRE_WEIGHT (defs.h:62, jnode.h:139-153).
+  void print(jnid_t id) const { printNode(nodes_.at(id), width(id)); }
+  static void printNode(const sheep_jnode &x) { printNode(x, (size_t)1 + x.pst_weight); }
+  static void printNode(const sheep_jnode &x, size_t width) {
+    printf("%6zu:w%6zu:pre%6zu:pst        ->[%4zu]\n", width, (size_t)0, (size_t)x.pst_weight, (size_t)x.parent);
   }
 
  private:
@@ -398,22 +413,39 @@ class JNodeTable {
   jnid_t end_id_ = 0;
   mutable std::unique_ptr<DeviceArray<sheep_jnode>> dev_;
   mutable sheep_kids *kids_ = nullptr;
+  std::vector<uint32_t> widths_;
+  std::unique_ptr<DeviceArray<uint32_t>> wdev_;
 };
 
 // JTree(graph, seq) (jtree.h:111-122 + jtree.cpp:66-145): the map step.
 class JTree {
  public:
   JNodeTable jnodes;
-  JTree(const GraphWrapper &graph, const DeviceSequence &seq) {
+  // JTree::Options (jtree.h:84-107) as far as this build has them: make_kids and make_pst
+  // change nothing here (the kid table is made on demand, pst sets are never needed);
+  // make_jxn computes the true widths.  isValid: make_jxn needs make_pst and make_kids.
+  struct Options {
+    bool make_kids = false, make_pst = false, make_jxn = false;
+    bool isValid() const { return !make_jxn || (make_pst && make_kids); }
+  };
+  JTree(const GraphWrapper &graph, const DeviceSequence &seq) : JTree(graph, seq, Options()) {}
+  JTree(const GraphWrapper &graph, const DeviceSequence &seq, const Options &opts) {
+    if (!opts.isValid()) throw std::invalid_argument("JTree: make_jxn needs make_pst and make_kids");
     DeviceArray<sheep_jnode> t(seq.n);
     check(sheep_build_tree(ctx(), graph.records(), graph.numRecords(), seq.pos.get(), seq.pos_size, seq.n, t.get()));
     jnodes.assign_from_device(t, (jnid_t)seq.n, (jnid_t)seq.n);
+    if (opts.make_jxn) jnodes.computeWidths(graph.records(), graph.numRecords(), seq.pos.get(), seq.pos_size);
   }
   jnid_t size() const { return jnodes.size(); }
   // JTree::print (jtree.h:60-66): one line per jnid, "id:vid" and the node's print(id).
   // The jnid->vid map is the sequence itself (get_sequence, jtree.h:50-57: every vid of
   // the sequence holds a jnid, make_pad being the default, jtree.h:88).
-  void print(const std::vector<vid_t> &seq) const { printTree(jnodes.nodes(), size(), seq); }
+  void print(const std::vector<vid_t> &seq) const {
+    for (jnid_t id = 0; id != size(); ++id) {
+      printf("%4zu:%-8zu", (size_t)id, (size_t)seq.at(id));
+      jnodes.print(id);
+    }
+  }
   static void printTree(const std::vector<sheep_jnode> &nodes, jnid_t n, const std::vector<vid_t> &seq) {
     for (jnid_t id = 0; id != n; ++id) {
       printf("%4zu:%-8zu", (size_t)id, (size_t)seq.at(id));
