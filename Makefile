@@ -1,7 +1,7 @@
 # Build everything in-tree (the built .so / binaries travel to the GPU box with gpurun).
 #   make            libsheep_hip.so + CLIs + oracle (+ oracle/_ref if /root/reference exists)
 #   make hip        sheep_amd/lib/libsheep_hip.so (gfx950 only)
-#   make cli        sheep_amd/bin/{graph2tree,partition_tree,merge_trees,degree_sequence,rmat_gen}
+#   make cli        sheep_amd/bin/{graph2tree,partition_tree,merge_trees,degree_sequence,verify_tree}
 #   make oracle     oracle/lib/libsheep_oracle.so (test infrastructure)
 #   make ref        oracle/_ref/* (reference sources compiled in place; container only)
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -13,7 +13,7 @@ HIPSRC  := $(wildcard sheep_amd/csrc/*.hip)
 HIPOBJ  := $(patsubst sheep_amd/csrc/%.hip,build/hip/%.o,$(HIPSRC))
 HIPHDR  := $(wildcard sheep_amd/csrc/*.hpp) include/sheep_hip.h
 LIB     := sheep_amd/lib/libsheep_hip.so
-CLIS    := graph2tree partition_tree merge_trees degree_sequence
+CLIS    := graph2tree partition_tree merge_trees degree_sequence verify_tree
 CLIBIN  := $(addprefix sheep_amd/bin/,$(CLIS))
 CXX     ?= g++
 

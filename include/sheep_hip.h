@@ -32,6 +32,8 @@
  *   sheep_tree_widths             jtree.cpp:97 + jnode.h:230-260 (newUnion: the junction sets
  *                                 of graph2tree -k -e -j; here only their sizes, width(id))
  *   sheep_facts_widths            jnode.cpp:256-290 with those widths (width, fill, halo)
+ *   sheep_verify_*                jtree.cpp:238-300 (JTree::isValid, graph2tree -c) as it was
+ *                                 meant: the tree is the elimination tree of the records
  *   sheep_rmat_generate           (new) synthetic Graph500-style RMAT .dat records
  */
 #ifndef SHEEP_HIP_H
@@ -47,7 +49,7 @@ extern "C" {
 /* ABI version: raised whenever a public struct changes size or layout or an entry point its
  * signature (INTEGRATION.md "ABI versions" lists the changes).  sheep_abi_version() returns the
  * library's; a caller built against another header should refuse to run. */
-#define SHEEP_ABI_VERSION 7
+#define SHEEP_ABI_VERSION 8
 int sheep_abi_version(void);
 
 #define SHEEP_OK 0
@@ -407,9 +409,10 @@ int sheep_facts(sheep_ctx *ctx, const sheep_jnode *tree_dev, uint64_t n, sheep_f
  * dropped as the map drops them; a repeated edge counts once.  A neighbour >= pos_size of
  * a sequenced vertex is SHEEP_ERR_RANGE, as in sheep_build_tree.
  * tree_dev must be the tree of exactly these records under this sequence (a shard's tree,
- * or a merge with only one shard's records, gives meaningless counts).  That cannot be
- * verified in general; the call returns SHEEP_ERR_ARG when some edge's earlier end is not a
- * descendant of its later end.  n == 0, nrec == 0 and all-self-loop inputs give widths of 1.
+ * or a merge with only one shard's records, gives meaningless counts).  This call tests only
+ * part of that: it returns SHEEP_ERR_ARG when some edge's earlier end is not a descendant of
+ * its later end.  sheep_verify_tree (below) decides it exactly; call it first for a tree of
+ * unknown origin.  n == 0, nrec == 0 and all-self-loop inputs give widths of 1.
  * Synchronises (the error flags).  Timers: "widths" and its passes "widths_tour",
  * "widths_sort", "widths_lca", "widths_weights", "widths_sums". */
 int sheep_tree_widths(sheep_ctx *ctx, const sheep_xs1 *rec_dev, uint64_t nrec, const uint32_t *pos_dev,
@@ -420,6 +423,58 @@ int sheep_tree_widths(sheep_ctx *ctx, const sheep_xs1 *rec_dev, uint64_t nrec, c
  * width > 3, core by the reference's running-maximum rule.  width_dev == NULL: sheep_facts. */
 int sheep_facts_widths(sheep_ctx *ctx, const sheep_jnode *tree_dev, uint64_t n, const uint32_t *width_dev,
                        sheep_facts_t *out);
+
+/* ---- verify a tree against its graph (graph2tree -c) ----------------------------------
+ * Is tree_dev[0, n) the elimination tree of these records under this sequence?  (What the
+ * reference's JTree::isValid, jtree.cpp:238-300, means to check; its per-edge ancestor walk
+ * starts at index.at(X) where index.at(nbr) should stand, so it never runs.)  With the records
+ * in sequence positions (lo < hi; self-loops and records with an unsequenced end carry no edge,
+ * as in sheep_build_tree), the forest is that tree if and only if
+ *   1. structure  every parent is SHEEP_INVALID_ID or lies in (id, n);
+ *   2. descent    for every edge (lo, hi), hi is an ancestor of lo;
+ *   3. support    for every non-root v with parent p, some edge (x, p) has x in v's subtree;
+ *   4. pst        pst_weight[v] = the edges with lo == v plus the records whose only
+ *                 sequenced end is v (sheep_build_tree's count).
+ * The verdict counts the offenders of each class and names the smallest one: a node id, or
+ * for not_descendant a record's index in its sheep_verify_add call's rec_dev (with several
+ * adds: the smallest such index over the calls).  first_* is UINT64_MAX where the count is 0.  Every field is deterministic.
+ * When bad_parent != 0 the verdict is final after sheep_verify_begin: no tour is built from
+ * such a tree, sheep_verify_add does nothing (it does not look at the records), and the
+ * other three classes are not evaluated and read 0.
+ *   sheep_verify_begin   the structure pass and, when it holds, the kid table, the Euler tour
+ *                        and the subtree intervals, kept by the handle (24 B per node of HBM
+ *                        plus a kid table).  Synchronises.  tree_dev must stay unchanged and
+ *                        allocated until the handle is destroyed.
+ *   sheep_verify_add     one pass over one edge shard; once per shard, in any order.  The state
+ *                        is the support marks, the pst counts and the counters.  Every call
+ *                        takes the same sequence index.  Synchronises (the range flag): a
+ *                        neighbour >= pos_size of a sequenced vertex is SHEEP_ERR_RANGE, as in
+ *                        sheep_build_tree, and then the handle has no verdict
+ *                        (sheep_verify_finish returns SHEEP_ERR_RANGE too).
+ *   sheep_verify_finish  the pass over the nodes and the verdict (host; synchronises).  More
+ *                        shards may be added afterwards and the verdict asked for again.
+ *   sheep_verify_destroy frees the handle (before or after a finish); the context must
+ *                        outlive its handles.  Several handles may be live on one context.
+ *   sheep_verify_tree    begin, one add, finish, destroy.
+ * n == 0 is valid.  nrec == 0 (or only self-loops) is valid when every node is a root with
+ * pst_weight 0.  Timers: "verify" and its passes "verify_structure", "verify_tour",
+ * "verify_records", "verify_finish". */
+typedef struct sheep_verify sheep_verify;
+typedef struct {
+  int32_t ok;                    /* 1: every count below is 0 */
+  uint64_t bad_parent;           /* nodes whose parent is not later or not in range        */
+  uint64_t not_descendant;       /* records whose earlier end is not below their later end */
+  uint64_t unsupported;          /* non-roots whose subtree has no edge to their parent    */
+  uint64_t pst_mismatch;         /* nodes whose pst_weight is not the records' count       */
+  uint64_t first_bad_parent, first_not_descendant, first_unsupported, first_pst_mismatch;
+} sheep_verify_t;
+int sheep_verify_begin(sheep_ctx *ctx, const sheep_jnode *tree_dev, uint64_t n, sheep_verify **out);
+int sheep_verify_add(sheep_verify *v, const sheep_xs1 *rec_dev, uint64_t nrec, const uint32_t *pos_dev,
+                     uint64_t pos_size);
+int sheep_verify_finish(sheep_verify *v, sheep_verify_t *out);
+int sheep_verify_destroy(sheep_verify *v);
+int sheep_verify_tree(sheep_ctx *ctx, const sheep_xs1 *rec_dev, uint64_t nrec, const uint32_t *pos_dev,
+                      uint64_t pos_size, const sheep_jnode *tree_dev, uint64_t n, sheep_verify_t *out);
 
 /* ---- .dat partial loads (LLAMAGraph(filename, part, num_parts), graph_wrapper.h:43-63) ----
  * Host-only.  sheep_dat_range: records [*first_out, *first_out + *count_out) of a .dat file

@@ -16,6 +16,7 @@ Partition::print           :meth:`PartitionResult.print_text`  (partition.h:135-
 Partition::evaluate        :func:`evaluate`  (partition.cpp:428-521)
 JNodeTable::Facts          :func:`facts`  (jnode.cpp:256-290)
 JTree make_jxn / width(id) :func:`tree_widths`  (jtree.cpp:97, jnode.h:230-260)
+JTree::isValid             :func:`verify_tree`, :class:`TreeVerifier`  (jtree.cpp:238-300)
 =========================  ======================================================
 
 Device memory is torch-allocated (``torch.cuda``), streams are torch's current
@@ -41,7 +42,7 @@ INVALID_PART = -1
 DEGREE_MODES = {"llama": 0, "dat": 1, "net": 2}
 EVAL_GRAPH, EVAL_DOWN, EVAL_UP = 1, 2, 4
 
-ABI_VERSION = 7   # include/sheep_hip.h SHEEP_ABI_VERSION
+ABI_VERSION = 8   # include/sheep_hip.h SHEEP_ABI_VERSION
 _ERRORS = {-1: ValueError, -2: RuntimeError, -3: IndexError, -4: RuntimeError, -5: MemoryError}
 
 
@@ -65,6 +66,12 @@ class _Eval(ctypes.Structure):
 class _Facts(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in (
         "width", "root_cnt", "vert_height", "edge_height", "vert_cnt", "edge_cnt", "halo_id", "core_id", "fill")]
+
+
+class _Verify(ctypes.Structure):
+    _fields_ = [("ok", ctypes.c_int32)] + [(f, ctypes.c_uint64) for f in (
+        "bad_parent", "not_descendant", "unsupported", "pst_mismatch",
+        "first_bad_parent", "first_not_descendant", "first_unsupported", "first_pst_mismatch")]
 
 
 class Tuning(ctypes.Structure):
@@ -143,6 +150,11 @@ def lib() -> ctypes.CDLL:
         "sheep_facts": ([P, P, U64, ctypes.POINTER(_Facts)], I32),
         "sheep_tree_widths": ([P, P, U64, P, U64, P, U64, P], I32),
         "sheep_facts_widths": ([P, P, U64, P, ctypes.POINTER(_Facts)], I32),
+        "sheep_verify_begin": ([P, P, U64, ctypes.POINTER(P)], I32),
+        "sheep_verify_add": ([P, P, U64, P, U64], I32),
+        "sheep_verify_finish": ([P, ctypes.POINTER(_Verify)], I32),
+        "sheep_verify_destroy": ([P], I32),
+        "sheep_verify_tree": ([P, P, U64, P, U64, P, U64, ctypes.POINTER(_Verify)], I32),
         "sheep_eval_sizes": ([I32, I32, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)], I32),
         "sheep_eval_num_parts": ([P, P, U64, ctypes.POINTER(ctypes.c_int32)], I32),
         "sheep_eval_shard": ([P, P, U64, P, U64, P, I32, I32, P, P], I32),
@@ -659,6 +671,79 @@ def tree_widths(records, seq: Sequence, tree, nrec: int | None = None, ctx: Cont
     _check(lib().sheep_tree_widths(ctx.handle, _ptr(records), nrec, _ptr(seq.pos), seq.pos_size, _ptr(tree), n,
                                    _ptr(out)))
     return out[:n]
+
+
+NO_ID = 0xFFFFFFFFFFFFFFFF   # a VerifyResult first_* field without an offender
+
+
+@dataclass
+class VerifyResult:
+    """sheep_verify_t: the counts of each class of offender and the smallest one (a node id;
+    a record index for not_descendant; NO_ID where the count is 0).  With bad_parent != 0 the
+    other three classes are not evaluated and read 0."""
+    ok: bool
+    bad_parent: int
+    not_descendant: int
+    unsupported: int
+    pst_mismatch: int
+    first_bad_parent: int
+    first_not_descendant: int
+    first_unsupported: int
+    first_pst_mismatch: int
+
+    @classmethod
+    def _of(cls, out: "_Verify") -> "VerifyResult":
+        return cls(bool(out.ok), *[getattr(out, f) for f, _ in _Verify._fields_[1:]])
+
+    def __bool__(self):
+        return self.ok
+
+
+def verify_tree(records, seq: Sequence, tree, nrec: int | None = None, ctx: Context | None = None) -> VerifyResult:
+    """Is `tree` the elimination tree of exactly these records under `seq` (graph2tree -c;
+    what JTree::isValid, jtree.cpp:238-300, means to check)?  sheep_verify_tree: later
+    parents, every edge's earlier end below its later end, every non-root's subtree adjacent
+    to its parent, pst_weight as the map counts it.  A neighbour >= pos_size of a sequenced
+    vertex raises IndexError, as in :func:`build_tree`."""
+    ctx = ctx or default_context()
+    nrec = records.shape[0] if nrec is None else nrec
+    out = _Verify()
+    _check(lib().sheep_verify_tree(ctx.handle, _ptr(records), nrec, _ptr(seq.pos), seq.pos_size, _ptr(tree),
+                                   tree.shape[0], ctypes.byref(out)))
+    return VerifyResult._of(out)
+
+
+class TreeVerifier:
+    """:func:`verify_tree` over edge shards: the structure pass and the tour once
+    (sheep_verify_begin), :meth:`add` once per shard in any order, :meth:`finish` for the
+    verdict.  `tree` must stay unchanged while the verifier lives (it is kept referenced)."""
+
+    def __init__(self, seq: Sequence, tree, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        self.seq, self.tree = seq, tree
+        h = ctypes.c_void_p()
+        _check(lib().sheep_verify_begin(self.ctx.handle, _ptr(tree), tree.shape[0], ctypes.byref(h)))
+        self.handle = h
+
+    def add(self, records, nrec: int | None = None):
+        nrec = records.shape[0] if nrec is None else nrec
+        _check(lib().sheep_verify_add(self.handle, _ptr(records), nrec, _ptr(self.seq.pos), self.seq.pos_size))
+
+    def finish(self) -> VerifyResult:
+        out = _Verify()
+        _check(lib().sheep_verify_finish(self.handle, ctypes.byref(out)))
+        return VerifyResult._of(out)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().sheep_verify_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------------

@@ -30,8 +30,10 @@ static double seconds_since(std::chrono::steady_clock::time_point t) {
   return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t).count() / 1000.0;
 }
 
-// JTree::isValid (jtree.cpp:238-300) as far as it checks anything (the per-edge ancestor
-// checks are vacuous there): index count == verts, parents later and in range.
+// JTree::isValid (jtree.cpp:238-300) as far as the reference checks anything (the per-edge
+// ancestor checks are vacuous there): index count == verts, parents later and in
+// range.  Only rank 0 of a reduced world of several ranks still uses it (run_world); every
+// other -c runs the verifier (JTree::isValid in sheep.hpp, sheep_verify_tree).
 static bool tree_valid(const std::vector<sheep_jnode> &nodes, uint64_t n, uint64_t vert_cnt) {
   bool ok = vert_cnt == n;
   for (uint64_t id = 0; ok && id != n; ++id) {
@@ -191,7 +193,21 @@ static int run_world(World &w, const char *graph_filename, bool use_mpi_sort, bo
         if (n) rk[i].tree.download(h.data(), n);
       }
       if (do_print) JTree::printTree(h, (jnid_t)n, seq_host);
-      if (do_validate) printf(tree_valid(h, n, f.f.vert_cnt) ? "Tree is valid.\n" : "ERROR: Tree is not valid.\n");
+      if (do_validate) {
+        // a rank that holds its own shard's tree checks it against its own records; rank 0
+        // after -r holds the merged tree but only its shard's records (a distributed verify
+        // is not built): the structural check
+        bool ok;
+        if (use_mpi_reduce && rk[i].rank == 0) {
+          ok = tree_valid(h, n, f.f.vert_cnt);
+        } else {
+          sheep_verify_t v;
+          check(sheep_verify_tree(w.ctx(i), rk[i].rec.get(), rk[i].nrec, rk[i].pos.get(), pos_size, rk[i].tree.get(),
+                                  n, &v));
+          ok = v.ok != 0;
+        }
+        printf(ok ? "Tree is valid.\n" : "ERROR: Tree is not valid.\n");
+      }
     }
   }
   if (verbose) printf("Finished in: %f seconds\n", seconds_since(start_point));
@@ -334,11 +350,8 @@ int main(int argc, char *argv[]) {
     if (verbose) printf("Built in: %f seconds\n", seconds_since(start_point));
     if (do_faqs) tree.jnodes.getFacts().print();
     if (do_print) tree.print(seq.host());   // graph2tree.cpp:229-230
-    if (do_validate) {
-      const Facts f = tree.jnodes.getFacts();
-      printf(tree_valid(tree.jnodes.nodes(), tree.size(), f.f.vert_cnt) && f.f.vert_cnt == seq.n
-                 ? "Tree is valid.\n" : "ERROR: Tree is not valid.\n");
-    }
+    if (do_validate)   // the tree of exactly this load's records (-l: this part's) under seq
+      printf(tree.isValid(graph, seq, jopts) ? "Tree is valid.\n" : "ERROR: Tree is not valid.\n");
     if (verbose) printf("Finished in: %f seconds\n", seconds_since(start_point));
   } catch (const std::out_of_range &e) {
     fprintf(stderr, "terminate called after throwing an instance of 'std::out_of_range'\n  what():  %s\n", e.what());

@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "tree_tour.hpp"
+#include "verify.hpp"
 
 namespace sheep {
 static thread_local std::string g_last_error;
@@ -67,10 +68,11 @@ using sheep::Error;
 // the caller's current device is restored on return.
 struct DeviceGuard {
   int prev = -1;
-  explicit DeviceGuard(const sheep_ctx *x) {
-    if (!x) return;
+  explicit DeviceGuard(const sheep_ctx *x) : DeviceGuard(x ? &x->c : nullptr) {}
+  explicit DeviceGuard(const sheep::Ctx *c) {
+    if (!c) return;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != x->c.device) HIP_CHECK(hipSetDevice(x->c.device));
+    if (prev != c->device) HIP_CHECK(hipSetDevice(c->device));
     else prev = -1;
   }
   ~DeviceGuard() {
@@ -536,6 +538,62 @@ int sheep_facts_widths(sheep_ctx *ctx, const sheep_jnode *tree, uint64_t n, cons
   NEED(ctx && out && (tree || !n), "null argument");
   sheep::tree_facts_widths(ctx->c, tree, n, width, out);
   API_END
+}
+
+int sheep_verify_begin(sheep_ctx *ctx, const sheep_jnode *tree, uint64_t n, sheep_verify **out) {
+  API_BEGIN
+  DeviceGuard dg(ctx);
+  NEED(ctx && out && (tree || !n), "null argument");
+  NEED(n < 0xFFFFFFFFull, "tree too large for 32-bit node ids");
+  sheep_verify *h = new sheep_verify();
+  try {
+    sheep::verify_begin(ctx->c, tree, n, h);
+  } catch (...) {
+    sheep::verify_free(h);
+    delete h;
+    throw;
+  }
+  *out = h;
+  API_END
+}
+
+int sheep_verify_add(sheep_verify *h, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *pos, uint64_t pos_size) {
+  API_BEGIN
+  NEED(h && (rec || !nrec) && (pos || !pos_size), "null argument");
+  DeviceGuard dg(h->ctx);
+  sheep::verify_add(h, rec, nrec, pos, pos_size);
+  API_END
+}
+
+int sheep_verify_finish(sheep_verify *h, sheep_verify_t *out) {
+  API_BEGIN
+  NEED(h && out, "null argument");
+  DeviceGuard dg(h->ctx);
+  sheep::verify_finish(h, out);
+  API_END
+}
+
+int sheep_verify_destroy(sheep_verify *h) {
+  API_BEGIN
+  if (!h) return SHEEP_OK;
+  DeviceGuard dg(h->ctx);
+  sheep::verify_free(h);
+  delete h;
+  API_END
+}
+
+int sheep_verify_tree(sheep_ctx *ctx, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *pos, uint64_t pos_size,
+                      const sheep_jnode *tree, uint64_t n, sheep_verify_t *out) {
+  if (!out) { sheep::set_error("null argument"); return SHEEP_ERR_ARG; }
+  sheep_verify *h = nullptr;
+  int rc = sheep_verify_begin(ctx, tree, n, &h);
+  if (rc != SHEEP_OK) return rc;
+  rc = sheep_verify_add(h, rec, nrec, pos, pos_size);
+  if (rc == SHEEP_OK) rc = sheep_verify_finish(h, out);
+  const std::string msg = sheep_last_error();   // (the failure's message, not the destroy's)
+  sheep_verify_destroy(h);
+  if (rc != SHEEP_OK) sheep::set_error(msg.c_str());
+  return rc;
 }
 
 int sheep_parse_net(sheep_ctx *ctx, const char *text, uint64_t bytes, int skip_comments, sheep_xs1 *out, uint64_t cap,

@@ -217,6 +217,22 @@ __global__ void k_tpos(const uint32_t *__restrict__ parent, uint64_t n, const ui
   }
 }
 
+// The tour positions of v's proper descendants' down arcs: [ilo, ihi).  A root's span is
+// its kids' (roots have no arcs of their own).
+__global__ void k_intervals(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ koff,
+                              const uint32_t *__restrict__ kids, const uint32_t *__restrict__ tD,
+                              const uint32_t *__restrict__ tU, uint64_t n, uint32_t *__restrict__ ilo,
+                              uint32_t *__restrict__ ihi) {
+  const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+  for (uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; v < n; v += stride) {
+    uint32_t a = 0, b = 0;
+    if (parent[v] != INVALID) { a = tD[v] + 1; b = tU[v]; }
+    else if (koff[v] < koff[v + 1]) { a = tD[kids[koff[v]]]; b = tU[kids[koff[v + 1] - 1]] + 1; }
+    ilo[v] = a;
+    ihi[v] = b;
+  }
+}
+
 __global__ void k_gather_u32(const uint32_t *__restrict__ src, const uint32_t *__restrict__ idx, uint64_t m,
                              uint32_t *__restrict__ dst) {
   const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
@@ -384,6 +400,14 @@ void build_tour(Ctx &c, sheep_kids *k, Tour &t) {
   }
   hipLaunchKernelGGL(k_tpos, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, k->parent, n, owner, loff, sa,
                      (uint32_t)t.A, t.tD, t.tU);
+  LAUNCH_CHECK();
+}
+
+void tour_intervals(Ctx &c, const sheep_kids *k, const Tour &t, uint32_t *ilo, uint32_t *ihi) {
+  if (!k->n) return;
+  hipLaunchKernelGGL(k_intervals, dim3(grid_for(k->n)), dim3(BLOCK), 0, c.stream, (const uint32_t *)k->parent,
+                     (const uint32_t *)k->koff, (const uint32_t *)k->kids, (const uint32_t *)t.tD,
+                     (const uint32_t *)t.tU, k->n, ilo, ihi);
   LAUNCH_CHECK();
 }
 

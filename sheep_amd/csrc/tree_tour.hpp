@@ -30,6 +30,10 @@ struct Tour {
 void build_kids(Ctx &c, const sheep_jnode *tree, uint64_t n, sheep_kids *k);
 void release_kids(Ctx *c, sheep_kids *k);
 void build_tour(Ctx &c, sheep_kids *k, Tour &t);
+// ilo[v], ihi[v]: the tour positions of v's proper descendants' down arcs are those in
+// [ilo[v], ihi[v]) (a root's span is its kids'; empty for a node without kids).  u is a proper
+// descendant of v exactly when ilo[v] <= tD[u] < ihi[v] (a root's tD is INVALID: below nothing).
+void tour_intervals(Ctx &c, const sheep_kids *k, const Tour &t, uint32_t *ilo, uint32_t *ihi);
 // generic helpers
 void gather_u32(Ctx &c, const uint32_t *src, const uint32_t *idx, uint64_t m, uint32_t *dst);
 

@@ -60,22 +60,6 @@ __global__ __launch_bounds__(BLOCK) void k_w_keys(const sheep_xs1 *__restrict__ 
   if (__any(stray) && (threadIdx.x & 63) == 0) atomicAdd(&flags[1], 1ull);
 }
 
-// The tour positions of v's proper descendants' down arcs: [ilo, ihi).  A root's span is
-// its kids' (roots have no arcs of their own).
-__global__ void k_w_intervals(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ koff,
-                              const uint32_t *__restrict__ kids, const uint32_t *__restrict__ tD,
-                              const uint32_t *__restrict__ tU, uint64_t n, uint32_t *__restrict__ ilo,
-                              uint32_t *__restrict__ ihi) {
-  const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
-  for (uint64_t v = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; v < n; v += stride) {
-    uint32_t a = 0, b = 0;
-    if (parent[v] != INVALID) { a = tD[v] + 1; b = tU[v]; }
-    else if (koff[v] < koff[v + 1]) { a = tD[kids[koff[v]]]; b = tU[kids[koff[v + 1] - 1]] + 1; }
-    ilo[v] = a;
-    ihi[v] = b;
-  }
-}
-
 // Level 0: the node the tour stands on after each arc (a down arc into c: c; an up arc out
 // of c: its parent).
 __global__ void k_w_level0(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ tD,
@@ -200,10 +184,7 @@ void tree_widths(Ctx &c, const sheep_xs1 *rec, uint64_t nrec, const uint32_t *po
     {
       TimedRegion tr(c, "widths_tour", 8 * n);
       build_tour(c, &k, t);
-      hipLaunchKernelGGL(k_w_intervals, dim3(grid_for(n)), dim3(BLOCK), 0, c.stream, (const uint32_t *)k.parent,
-                         (const uint32_t *)k.koff, (const uint32_t *)k.kids, (const uint32_t *)t.tD,
-                         (const uint32_t *)t.tU, n, ilo, ihi);
-      LAUNCH_CHECK();
+      tour_intervals(c, &k, t, ilo, ihi);
     }
     const uint64_t A = t.A;
     const int sh = bits_for(A ? A - 1 : 0), end_bit = sh + bits_for(n);

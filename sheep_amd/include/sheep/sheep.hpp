@@ -437,6 +437,30 @@ class JTree {
     if (opts.make_jxn) jnodes.computeWidths(graph.records(), graph.numRecords(), seq.pos.get(), seq.pos_size);
   }
   jnid_t size() const { return jnodes.size(); }
+  // JTree::isValid (jtree.cpp:238-300) as it was meant: this tree is the elimination tree of
+  // the graph's records under seq (sheep_verify_tree: later parents, every edge's earlier end
+  // below its later end, every non-root's subtree adjacent to its parent, pst weights).  The
+  // reference's own loop walks from index.at(X) instead of index.at(nbr) and checks nothing.
+  // opts: unused (no pst or jxn sets exist to check).  verdict: the counts, when asked for.
+  bool isValid(const GraphWrapper &graph, const DeviceSequence &seq, const Options &opts,
+               sheep_verify_t *verdict = nullptr) const {
+    (void)opts;
+    return isValid(jnodes, graph, seq, verdict);
+  }
+  // The same for a table that no JTree built (a loaded .tre).
+  static bool isValid(const JNodeTable &nodes, const GraphWrapper &graph, const DeviceSequence &seq,
+                      sheep_verify_t *verdict = nullptr) {
+    sheep_verify_t v{};
+    v.first_bad_parent = v.first_not_descendant = v.first_unsupported = v.first_pst_mismatch = UINT64_MAX;
+    if (nodes.size() != seq.n) {   // valid_indices != faq.vert_cnt (jtree.cpp:246); no class is counted
+      if (verdict) *verdict = v;
+      return false;
+    }
+    check(sheep_verify_tree(ctx(), graph.records(), graph.numRecords(), seq.pos.get(), seq.pos_size, nodes.device(),
+                            nodes.size(), &v));
+    if (verdict) *verdict = v;
+    return v.ok != 0;
+  }
   // JTree::print (jtree.h:60-66): one line per jnid, "id:vid" and the node's print(id).
   // The jnid->vid map is the sequence itself (get_sequence, jtree.h:50-57: every vid of
   // the sequence holds a jnid, make_pad being the default, jtree.h:88).
